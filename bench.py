@@ -7,7 +7,13 @@ whole hot path (input cast -> stem -> 16 Res2Net bottlenecks -> stats-pool ->
 BN/dense/BN head); with N > 1 ranks each step also all-gathers the step's
 embeddings over RCCL (the cohort assembly of eval_inference_model.sh:38-39).
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+A plain run sets up, warms up, times the steps and prints the headline line.
+`--full` adds everything else to that line: the per-kernel profile and roofline,
+the CPU baseline with the fp32 like-for-like line, and the synthetic-speaker
+EER delta.  `--dump-outputs DIR` writes the embeddings of the last timed step.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--full]
+                       [--dump-outputs DIR]
        torchrun --nproc-per-node N bench.py --gpus N ...
 """
 
@@ -381,6 +387,25 @@ def _progress(msg):
         print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: write every array as out_dir/<name>.npy (float32 or
+    float64), at most `limit` bytes in all.  An array over its share of the
+    limit is written as a fixed sample of its flattened elements (seed 0,
+    sorted indices), the same elements on every run of the same shape."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = limit // max(len(arrays), 1) - 4096      # room for the .npy header
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:
+            keep = share // a.itemsize
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1,
@@ -393,14 +418,27 @@ def main():
     ap.add_argument("--frames", type=int, default=200)
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-eer", action="store_true", help="skip the synthetic-speaker EER delta")
-    ap.add_argument("--dump-ops", action="store_true", help="print per-op timing to stderr")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the per-kernel profile (roofline, "
+                         "kernels), the CPU baseline with the fp32 like-for-like line and the "
+                         "synthetic-speaker EER delta, and add them to the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the embeddings of the last timed step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline (and the EER delta beside it)")
+    ap.add_argument("--no-eer", action="store_true",
+                    help="with --full: skip the synthetic-speaker EER delta")
+    ap.add_argument("--dump-ops", action="store_true",
+                    help="with --full: print per-op timing to stderr")
     ap.add_argument("--cache-dir", default=os.environ.get("VOXEMB_CACHE", "/tmp/voxemb_cache"))
     ap.add_argument("--stub-extractor", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_ops and not args.full:
+        ap.error("--dump-ops prints the per-kernel profile: pass --full")
 
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:
@@ -476,6 +514,43 @@ def main():
     value = world * B * args.steps / el
     _progress(f"timed {args.steps} steps: {ms_per_step:.3f} ms per step")
 
+    if args.dump_outputs and rank == 0:
+        # what the caller of the timed path holds after the last step
+        arrays = {"embeddings": out.cpu().numpy()}
+        if dist_on:
+            arrays["gathered"] = torch.stack(gathered).cpu().numpy()
+        dump_outputs(args.dump_outputs, arrays)
+
+    roof, extra, cpu, eer = None, {}, None, None
+    if args.full:
+        roof, extra = kernel_report(ex, x, stream, args, rank)
+        cpu, eer = reference_report(x, stream, args, rank, world, blob, value)
+
+    if rank == 0:
+        line = {
+            "metric": "utterances/sec (80-d FBANK, T=200) embedding extraction",
+            "value": round(value, 1), "unit": "utterances/sec", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": args.precision, "data": "synthetic (seeded N(0,1) FBANK, random-init "
+                                            "calibrated weights)",
+            "config": {"workload": f"{args.model} {F}x{T} extraction", "global_batch": B * world,
+                       "per_gpu_batch": B, "frames": T, "feat_dim": F,
+                       "parallelism": f"dp{world}" + (" + RCCL all-gather" if dist_on else "")},
+        }
+        if args.full:
+            line.update({"roofline": roof, "cpu_baseline": cpu, "eer_delta_vs_fp32": eer, **extra})
+        print(json.dumps(line))
+    if dist_on:
+        dist.barrier()
+        dist.destroy_process_group()
+    ex.close()
+
+
+def kernel_report(ex, x, stream, args, rank):
+    """--full: (roofline, the other per-kernel entries of the line) from a
+    profiled forward of the timed workload."""
+    B, T, F = args.batch, args.frames, args.feat_dim
     # ---- per-kernel timing (HIP events around every launch, same stream)
     prof = ex.profile(x, reps=5, stream=stream)
     if args.dump_ops and rank == 0:
@@ -549,7 +624,16 @@ def main():
                                         "frac": round(gbs / PEAK_HBM_GBS, 4),
                                         "traffic": traffic("stats_pool_k"),
                                         "bytes_per_launch": pool["bytes"] / pool["n"]}
+    return roof, extra
 
+
+def reference_report(x, stream, args, rank, world, blob, value):
+    """--full: (cpu_baseline, eer_delta_vs_fp32) of the line, the comparisons
+    with the CPU oracle and the fp32 path; None where they do not apply."""
+    import torch
+    from voxsrc2020_speaker_verification_amd.extractor import Extractor
+    B, T, F = args.batch, args.frames, args.feat_dim
+    dev = x.device
     cpu = None
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         _progress("CPU baseline (bounded sample) and the fp32 like-for-like line")
@@ -575,34 +659,13 @@ def main():
             cpu["ratio_bf16_to_cpu"] = round(value / cpu["value"], 2)
 
     eer = None
-    # beside the CPU baseline (both reference comparisons; the profiling runs pass
-    # --no-cpu-baseline and so keep their dispatch lists to the timed workload)
+    # beside the CPU baseline (both reference comparisons; --no-cpu-baseline keeps a
+    # --full run's dispatch list to the timed workload and its per-kernel profile)
     if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.no_eer \
             and args.model == "res2net50_w24_s4_c32" and args.precision == "bf16":
         _progress("synthetic-speaker EER delta")
         eer = eer_delta(dev.index, F=F)
-
-    if rank == 0:
-        line = {
-            "metric": "utterances/sec (80-d FBANK, T=200) embedding extraction",
-            "value": round(value, 1), "unit": "utterances/sec", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": args.precision, "data": "synthetic (seeded N(0,1) FBANK, random-init "
-                                            "calibrated weights)",
-            "config": {"workload": f"{args.model} {F}x{T} extraction", "global_batch": B * world,
-                       "per_gpu_batch": B, "frames": T, "feat_dim": F,
-                       "parallelism": f"dp{world}" + (" + RCCL all-gather" if dist_on else "")},
-            "roofline": roof,
-            "cpu_baseline": cpu,
-            "eer_delta_vs_fp32": eer,
-            **extra,
-        }
-        print(json.dumps(line))
-    if dist_on:
-        dist.barrier()
-        dist.destroy_process_group()
-    ex.close()
+    return cpu, eer
 
 
 if __name__ == "__main__":

@@ -13,7 +13,7 @@ for r in $(seq 1 $ROUNDS); do
   for name in $LIBS; do
     lib=$P/libvoxemb_$name.so; [ "$name" = cur ] && lib=$P/libvoxemb.so
     out=gpurun_out/$TAG/${name}_$r
-    VOXEMB_LIB=$lib timeout -k 10 200 python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --dump-ops ${BENCH_ARGS} \
+    VOXEMB_LIB=$lib timeout -k 10 200 python3 bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --dump-ops ${BENCH_ARGS} \
       > $out.json 2> ${out}_ops.txt || { echo "$name rc=$?"; exit 1; }
     ops=$(awk -v re="$OPS" '$0 ~ re {s+=$1; n++} END {printf "%d ops %.1f us", n, s}' ${out}_ops.txt)
     python3 -c "import json; d=json.load(open('$out.json')); print('$name', $r, d['value'], d['ms_per_step'], '$ops')"

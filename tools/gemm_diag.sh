@@ -6,6 +6,6 @@
 export VOXEMB_LIB=${VOXEMB_LIB:-$PWD/voxsrc2020_speaker_verification_amd/libvoxemb_diag.so}
 export TMPDIR=/tmp
 for v in ${VARS:-0 11 12 14 13 15 16}; do
-  VOXEMB_GEMM_VAR=$v timeout -k 10 120 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --dump-ops \
+  VOXEMB_GEMM_VAR=$v timeout -k 10 120 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --dump-ops \
     > gpurun_out/diag_v$v.json 2> gpurun_out/diag_v$v.ops || exit $?
 done

@@ -1,4 +1,4 @@
-"""Compare per-op-kind totals of bench.py --dump-ops stderr dumps: ops_compare.py a.txt b.txt ..."""
+"""Compare per-op-kind totals of bench.py --full --dump-ops stderr dumps: ops_compare.py a.txt b.txt ..."""
 import sys
 from collections import defaultdict
 

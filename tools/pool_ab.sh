@@ -14,7 +14,7 @@ for v in 1 2 3; do
 done
 for r in 0 1; do for v in 0 1 2 3; do
   L=$P/libvoxemb.so; [ $v -gt 0 ] && L=$P/libvoxemb_pool$v.so
-  VOXEMB_LIB=$L timeout -k 10 200 python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --dump-ops \
+  VOXEMB_LIB=$L timeout -k 10 200 python3 bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --dump-ops \
     > gpurun_out/pool/b${v}_$r.json 2> gpurun_out/pool/o${v}_$r.txt || { echo "bench v$v rc=$?"; exit 1; }
   echo "v$v run$r: $(python3 -c "import json; d=json.load(open('gpurun_out/pool/b${v}_$r.json')); print(d['value'], d['ms_per_step'])") pool: $(grep -i ' pool' gpurun_out/pool/o${v}_$r.txt | awk '{printf "%s ", $1}')"
 done; done

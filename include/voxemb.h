@@ -85,8 +85,10 @@ int vox_embed_device(vox_model* m, const float* d_x, int n, int t, int f,
  * pool averages its lens[i] (downsampled) rows.  So chunks of different
  * lengths share one batch and one resident plan keyed on (n, t) -- what the
  * streaming extractor buckets real length distributions into.  res2net models
- * without attentive pooling and tdnn models, VOX_BF16; other plans (dpn68, the
- * attentive models, fp32) return VOX_EINVAL.
+ * (plain or attentive statistics pooling: the attentive pool's softmax, mean
+ * and std run over the utterance's own rows) and tdnn models, VOX_BF16; other
+ * plans (dpn68, fp32, a geometry with a kernel that does not mask) return
+ * VOX_EINVAL.
  * _device: d_lens is a device int32 [n] array (read in stream order);
  * vox_embed_lens: host buffers, lens checked on the host. */
 int vox_embed_device_lens(vox_model* m, const float* d_x, int n, int t, int f,
@@ -234,6 +236,15 @@ int vox_debug_read(void* dst, const void* d_src, size_t bytes);
 /* sizeof of an internal kernel parameter struct (0 = BneckParams, 1 = GconvParams),
  * for tests that launch a kernel through a ctypes mirror of it; -1 otherwise. */
 int64_t vox_debug_struct_size(int which);
+/* The attentive-pooling tail kernel on its own (tests): x NHWC [n,h,w,c]
+ * (dtype VOX_FP32 or VOX_BF16), logits float32 [n,h,w,c]; softmax over h of
+ * the logits, weighted mean and std of x, no head BN; out [n, w*2c] float32
+ * with feature index w*2c + {c | c+C}.  d_lens (device int32 [n], or NULL):
+ * utterance i pools its first min(h, ceil(d_lens[i] / 2^vsh)) rows only and
+ * reads no other -- the bits of a launch on that utterance alone at that h.
+ * Device pointers; asynchronous on `stream`. */
+int vox_debug_att_pool(const void* d_x, const float* d_logits, const int* d_lens, int vsh, int n,
+                       int h, int w, int c, int dtype, float eps, float* d_out, void* stream);
 
 /* ---- host-side Kaldi I/O (no Kaldi binaries needed) --------------------- */
 int vox_sliding_cmn(const float* in, int t, int f, int cmn_window, int center,

@@ -17,6 +17,7 @@ ARCH = os.environ.get("VOX_OFFLOAD_ARCH", "gfx950")
 
 SOURCES = [
     ("kernels.hip", ["-O3"]),
+    ("attpool.hip", ["-O3"]),
     ("bneck.hip", ["-O3"]),
     ("asnorm.hip", ["-O3"]),
     ("gemm.hip", ["-O3"]),

@@ -197,7 +197,7 @@ struct Op {
   const float* in_mean = nullptr;  // type 2: input BN+ReLU fused into the pool (DPN68)
   const float* in_inv = nullptr;
   int cin = 0;
-  // ragged batches (types 11, 2, 3): per-utterance frames + this op's shift
+  // ragged batches (types 11, 2, 3, 17): per-utterance frames + this op's shift
   const int* vlen = nullptr; int vsh = 0;
   double flops = 0, bytes = 0;
 };
@@ -927,6 +927,11 @@ static void emit_pool(Builder& B, Act x, float* out, const BNW& bn, const BNW* i
 //   Bnw = S W1[C:3C]                        (fp32 1x1 over the N*W rows)
 //   H = tanh(x W1[:C] + Bnw)                (fp32 1x1 + bias/tanh kernel)
 //   L = H W2 ; softmax over time ; weighted mean/std ; head BN -> pooled
+// Ragged batches: both pools take each utterance's valid rows only (B.vlen /
+// B.vsh); everything between them is per pixel -- the copy, the bias + tanh and
+// the three fp32 1x1 convs, whose conv_igemm accumulates a pixel's K in one
+// order whatever the tile shape picked from M -- so a padded pixel can only
+// dirty its own logit, which the pool never reads.
 static void emit_att_pool(Builder& B, Act x, float* pooled, Slot free_s) {
   vox_model* m = B.m;
   const int n = x.N, H = x.H, W = x.W, C = x.C, A = m->att_a.cout;
@@ -934,10 +939,15 @@ static void emit_att_pool(Builder& B, Act x, float* pooled, Slot free_s) {
   float* bnw = (float*)B.base(S_PART, (size_t)n * W * A * 4);
   float* hb = (float*)B.base(S_SC, (size_t)n * H * W * A * 4);
   float* lg = (float*)B.base(free_s, (size_t)n * H * W * C * 4);
+  // the attention MLP's convs are per pixel and carry no lengths: emit_conv's
+  // copy of B.vlen is cleared, so that no conv kernel can ever index the n
+  // frame counts with att_b's n * W pseudo-utterances
+  auto no_lens = [&] { B.ops->back().cp.vlen = nullptr; B.ops->back().cp.vsh = 0; };
   {
     Op op;
     op.kind = OP_POOL;
     op.type = 2;
+    op.vlen = B.vlen; op.vsh = B.vsh;
     op.src = x.p; op.N = n; op.H = H; op.W = W; op.C = C;
     op.mean = nullptr; op.inv = nullptr; op.out = S;
     op.bytes = (double)es_of(m) * n * H * W * C + 4.0 * n * W * 2 * C;
@@ -945,6 +955,7 @@ static void emit_att_pool(Builder& B, Act x, float* pooled, Slot free_s) {
   }
   emit_conv(B, m->att_b, Act{S, 2 * C, n * W, 1, 1, 2 * C}, nullptr, 0, 1, 1, 1, 1, 0, 0, 1, 1, bnw,
             A, 0, nullptr, 0, nullptr, 0, 1 << 30, nullptr, nullptr, F32);
+  no_lens();
   const float* x32 = (const float*)x.p;
   if (m->dt == BF16) {
     float* xc = (float*)B.base(S_A, (size_t)n * H * W * C * 4);
@@ -958,6 +969,7 @@ static void emit_att_pool(Builder& B, Act x, float* pooled, Slot free_s) {
   }
   emit_conv(B, m->att_a, Act{x32, C, n, H, W, C}, nullptr, 0, 1, 1, 1, 1, 0, 0, H, W, hb, A, 0,
             nullptr, 0, nullptr, 0, 1 << 30, nullptr, nullptr, F32);
+  no_lens();
   {
     Op op;
     op.kind = OP_OTHER;
@@ -968,9 +980,11 @@ static void emit_att_pool(Builder& B, Act x, float* pooled, Slot free_s) {
   }
   emit_conv(B, m->att_2, Act{hb, A, n, H, W, A}, nullptr, 0, 1, 1, 1, 1, 0, 0, H, W, lg, C, 0,
             nullptr, 0, nullptr, 0, 1 << 30, nullptr, nullptr, F32);
+  no_lens();
   Op op;
   op.kind = OP_POOL;
   op.type = 17;
+  op.vlen = B.vlen; op.vsh = B.vsh;
   op.src = x.p; op.part = lg; op.N = n; op.H = H; op.W = W; op.C = C;
   op.mean = (const float*)m->head_bn1.mean->p;
   op.inv = (const float*)m->head_bn1.inv->p;
@@ -1759,9 +1773,14 @@ static bool ragged_ok(const Op& op, DType dt) {
     case 12: case 13: case 14: case 22: case 24:   // bneck / chain / stride-2 row kernels
     case 20: case 26: case 28: case 30:            // 3x3 branch kernels
     case 1: case 2: case 4:                        // split-K reduce, stats pool, input cast
+    case 15: case 16:                              // attention tail: bf16 -> fp32 copy, bias + tanh
+    case 17:                                       // (elementwise), softmax-weighted pool (masked)
       return true;
     case 3: return op.C % 8 == 0 && op.lds % 8 == 0 && op.ldd % 8 == 0;   // avgpool3s2_v8
-    case 5: return op.kind == OP_HEAD;             // the fp32 head dense
+    case 5:                                        // the fp32 head dense; fp32 1x1 stride-1 convs
+      return op.kind == OP_HEAD ||                 // (the attention MLP): per pixel
+             (op.cp.kh == 1 && op.cp.kw == 1 && op.cp.sh == 1 && op.cp.sw == 1 && op.cp.ph == 0 &&
+              op.cp.pw == 0 && !op.cp.in_mean && !op.cp.x2 && !op.cp.res);
     case 21:                                       // 1x1 (per pixel) or the TDNN's taps
       if (op.cp.kh > 1)                            // GS_TAPS: the tap rows masked (gemm_wide.hip)
         return op.cp.kw == 1 && op.cp.W == 1 && op.cp.wblk && !op.cp.in_mean && !op.cp.res;
@@ -1778,8 +1797,8 @@ static int build_plan(vox_model* m, const float* x, int n, int t, float* out, bo
     m->plan.clear();
     m->taps.clear();
     if (rag) {
-      if ((m->family != "res2net" && m->family != "tdnn") || m->att)
-        return fail(VOX_EINVAL, "per-utterance lengths: res2net (without attentive pooling) and "
+      if (m->family != "res2net" && m->family != "tdnn")
+        return fail(VOX_EINVAL, "per-utterance lengths: res2net (plain or attentive pooling) and "
                                 "tdnn models only");
       B.vlen = (const int*)B.base(S_LEN, (size_t)n * 4);
     }
@@ -1863,7 +1882,7 @@ static hipError_t run_op(vox_model* m, const Op& op, hipStream_t s) {
     case 16: return launch_att_bias_tanh((float*)op.dst, (const float*)op.src, op.N, op.H, op.W, op.C, s);
     case 17:
       return launch_att_pool(m->dt, op.src, op.part, op.N, op.H, op.W, op.C, 1e-5f, op.mean,
-                             op.inv, op.out, s);
+                             op.inv, op.out, s, op.vlen, op.vsh);
     case 11:
       return launch_stem(m->dt, (const float*)op.src, op.N, op.H, op.W, op.part, op.C, op.mean,
                          op.inv, op.dst, s, op.vlen);
@@ -2361,6 +2380,17 @@ extern "C" int64_t vox_debug_struct_size(int which) {
 extern "C" int vox_debug_read(void* dst, const void* d_src, size_t bytes) {
   if (!dst || !d_src) return fail(VOX_EINVAL, "null argument");
   HIPCHK(hipMemcpy(dst, d_src, bytes, hipMemcpyDeviceToHost));
+  return VOX_OK;
+}
+
+extern "C" int vox_debug_att_pool(const void* d_x, const float* d_logits, const int* d_lens, int vsh,
+                                  int n, int h, int w, int c, int dtype, float eps, float* d_out,
+                                  void* stream) {
+  if (!d_x || !d_logits || !d_out || n <= 0 || h <= 0 || w <= 0 || c <= 0 || vsh < 0 || vsh > 16)
+    return fail(VOX_EINVAL, "bad attentive-pool arguments");
+  if (dtype != VOX_FP32 && dtype != VOX_BF16) return fail(VOX_EINVAL, "bad dtype");
+  HIPCHK(launch_att_pool(dtype == VOX_BF16 ? BF16 : F32, d_x, d_logits, n, h, w, c, eps, nullptr,
+                         nullptr, d_out, (hipStream_t)stream, d_lens, vsh));
   return VOX_OK;
 }
 

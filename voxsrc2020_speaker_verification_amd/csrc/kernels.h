@@ -195,12 +195,14 @@ hipError_t launch_stem(DType t, const float* x, int N, int H, int W, const float
 int conv_kstep(DType t);   // 32 (bf16) / 16 (fp32)
 // Attentive statistics pooling glue (fp32): bf16 -> fp32 copy; h = tanh(h +
 // b[n][w]) over [N][H][W][A]; softmax-over-time weighted mean/std (+ optional
-// head BN) into the NHWC-flattened [N][W*2C] feature vector.
+// head BN) into the NHWC-flattened [N][W*2C] feature vector (attpool.hip).
+// vlen / vsh (ragged batches): utterance n pools its valid_rows only, with the
+// bits of an H = valid_rows launch; the rows past them are never read.
 hipError_t launch_convert_bf16(const void* x, float* y, int64_t n, hipStream_t s);
 hipError_t launch_att_bias_tanh(float* h, const float* b, int N, int H, int W, int A, hipStream_t s);
 hipError_t launch_att_pool(DType t, const void* x, const float* lg, int N, int H, int W, int C,
                            float eps, const float* mean, const float* inv, float* out,
-                           hipStream_t s);
+                           hipStream_t s, const int* vlen = nullptr, int vsh = 0);
 int conv_vec(DType t);     // elements per 16-byte lane load: 8 / 4
 
 // Row-streamed grouped 3x3 conv + BN/ReLU input prologue (gconv.hip), DPN

@@ -1997,50 +1997,7 @@ hipError_t launch_att_bias_tanh(float* h, const float* b, int N, int H, int W, i
   return hipGetLastError();
 }
 
-// Softmax over time of the logits, weighted mean and std of x, head BN, NHWC
-// flatten (feature w*2C + j).  One thread per (n, w, c): coalesced over c.
-template <typename T>
-__global__ void att_pool_k(const T* __restrict__ x, const float* __restrict__ lg, int N, int H,
-                           int W, int C, float eps, const float* __restrict__ mean,
-                           const float* __restrict__ inv, float* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (int64_t)N * W * C) return;
-  const int c = (int)(i % C);
-  const int64_t nw = i / C;
-  const int w = (int)(nw % W);
-  const int64_t n = nw / W;
-  const int64_t base = (n * H * W + w) * C + c, st = (int64_t)W * C;
-  float mx = -INFINITY;
-  for (int t = 0; t < H; ++t) mx = fmaxf(mx, lg[base + t * st]);
-  float sum = 0.f;
-  for (int t = 0; t < H; ++t) sum += expf(lg[base + t * st] - mx);
-  float wm = 0.f, wss = 0.f;
-  for (int t = 0; t < H; ++t) {
-    const float wt = expf(lg[base + t * st] - mx) / sum;
-    const float xv = (float)x[base + t * st];
-    wm += xv * wt;
-    wss += xv * xv * wt;
-  }
-  const float sd = sqrtf(wss - wm * wm + eps);
-  float* o = out + n * W * 2 * C + (int64_t)w * 2 * C;
-  const int j0 = w * 2 * C + c, j1 = j0 + C;
-  o[c] = mean ? bn2d(wm, inv[j0], mean[j0]) : wm;
-  o[C + c] = mean ? bn2d(sd, inv[j1], mean[j1]) : sd;
-}
-
-hipError_t launch_att_pool(DType t, const void* x, const float* lg, int N, int H, int W, int C,
-                           float eps, const float* mean, const float* inv, float* out,
-                           hipStream_t s) {
-  const int64_t total = (int64_t)N * W * C;
-  const dim3 grid((unsigned)((total + 255) / 256));
-  if (t == BF16)
-    hipLaunchKernelGGL((att_pool_k<bf16_t>), grid, dim3(256), 0, s,
-                       reinterpret_cast<const bf16_t*>(x), lg, N, H, W, C, eps, mean, inv, out);
-  else
-    hipLaunchKernelGGL((att_pool_k<float>), grid, dim3(256), 0, s,
-                       reinterpret_cast<const float*>(x), lg, N, H, W, C, eps, mean, inv, out);
-  return hipGetLastError();
-}
+// (the softmax-over-time weighted pool itself: attpool.hip)
 
 }  // namespace vox
 

@@ -85,10 +85,11 @@ int vox_embed_device(vox_model* m, const float* d_x, int n, int t, int f,
  * pool averages its lens[i] (downsampled) rows.  So chunks of different
  * lengths share one batch and one resident plan keyed on (n, t) -- what the
  * streaming extractor buckets real length distributions into.  res2net models
- * (plain or attentive statistics pooling: the attentive pool's softmax, mean
+ * (every published geometry: w24_s4 with a 32- or 64-channel stem, w8_s6_c16;
+ * plain or attentive statistics pooling: the attentive pool's softmax, mean
  * and std run over the utterance's own rows) and tdnn models, VOX_BF16; other
- * plans (dpn68, fp32, a geometry with a kernel that does not mask) return
- * VOX_EINVAL.
+ * plans (dpn68, fp32, a plan with a kernel that does not mask, such as the
+ * VOXEMB_NO_* fallbacks) return VOX_EINVAL.
  * _device: d_lens is a device int32 [n] array (read in stream order);
  * vox_embed_lens: host buffers, lens checked on the host. */
 int vox_embed_device_lens(vox_model* m, const float* d_x, int n, int t, int f,

@@ -1372,6 +1372,7 @@ static int build_res2net(Builder& B, const float* x, int n, int t, float* out) {
             q.inv[j] = (const float*)br.inv->p;
             fl += 2.0 * n * H * W * 9.0 * w * w;
           }
+          q.vlen = B.vlen; q.vsh = B.vsh;
           Op op;
           op.kind = OP_CONV;
           op.type = 10;
@@ -1769,7 +1770,8 @@ static void stash_current(vox_model* m) {
 static bool ragged_ok(const Op& op, DType dt) {
   if (dt != BF16) return false;
   switch (op.type) {
-    case 11: return op.C == 32;                    // stem_conv1_c32
+    case 11: return op.C != 10;                    // stem_conv1_c32 / stem_conv1 (not the DPN68 stem)
+    case 10:                                       // split_chain
     case 12: case 13: case 14: case 22: case 24:   // bneck / chain / stride-2 row kernels
     case 20: case 26: case 28: case 30:            // 3x3 branch kernels
     case 1: case 2: case 4:                        // split-K reduce, stats pool, input cast
@@ -1787,6 +1789,16 @@ static bool ragged_ok(const Op& op, DType dt) {
       return op.cp.kw == 1 && !op.cp.in_mean;
     case 9: case 18: case 29: case 8:              // 1x1 convs (per pixel)
       return op.cp.kh == 1 && op.cp.kw == 1 && !op.cp.in_mean;
+    case 0:                                        // conv_igemm, whole K in one pass: 1x1 (per
+      if (op.kind != OP_CONV || op.cp.in_mean || (op.cp.flags & EPI_PARTIAL) || op.cl.splitk > 1)
+        return false;                              // pixel) or the 3x3 whose VEC path masks its taps
+      if (op.cp.kh == 1 && op.cp.kw == 1) return op.cp.ph == 0 && op.cp.pw == 0;
+      return op.cp.kh == 3 && op.cp.kw == 3 && op.cl.vec && op.cp.groups == 1;
+    case 7:                                        // conv_win: its 1x1s only (per pixel; one tap, so
+      // whole-K and 32-channel-multiple chunks alike accumulate K in ascending 32-channel
+      // steps whatever tile M picked); its 3x3 window staging does not mask
+      return op.cp.kh == 1 && op.cp.kw == 1 && op.cp.ph == 0 && op.cp.pw == 0 && !op.cp.in_mean &&
+             (op.cp.win_kc == op.cp.Cin || op.cp.win_kc % 32 == 0);
   }
   return false;
 }

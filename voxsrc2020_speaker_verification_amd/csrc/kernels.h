@@ -189,6 +189,7 @@ int conv3_pipe_ok(const ConvParams& p);
 hipError_t launch_conv3_pipe(const ConvParams& p, int num_cu, hipStream_t s);
 // 1-input-channel 3x3 SAME stem + BN + ReLU from the fp32 features;
 // wts = [9][Cout] fp32 (bf16-rounded values in bf16 mode), Cout <= 64.
+// vlen (ragged batches): bf16 only, any Cout but the DPN68 stem's 10.
 hipError_t launch_stem(DType t, const float* x, int N, int H, int W, const float* wts, int Cout,
                        const float* mean, const float* inv, void* y, hipStream_t s,
                        const int* vlen = nullptr);

@@ -148,7 +148,10 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, f32x4 (&acc)[
 // Block = 4 waves stacked along pixels; a wave owns WCO x WPX 16x16 tiles.
 // The accumulator layout (col = lane&15 = pixel, rows 4*(lane>>4)+r = couts)
 // gives every lane 4 consecutive channels of one pixel in the epilogue.
-template <typename T, int WCO, int WPX, bool VEC>
+// RAG (bf16 VEC path, ragged batches): a pixel's taps at or past its own
+// utterance's valid rows are read as that utterance's zero padding.  A separate
+// instance, so that the fixed-shape kernels keep their code and registers.
+template <typename T, int WCO, int WPX, bool VEC, bool RAG = false>
 __global__ __launch_bounds__(256) void conv_igemm(ConvParams p) {
   typedef typename Tr<T>::frag frag;
   constexpr int VN = Tr<T>::VEC;
@@ -200,6 +203,10 @@ __global__ __launch_bounds__(256) void conv_igemm(ConvParams p) {
       cbeg = blockIdx.z * p.kchunk;
       cend = min(cbeg + p.kchunk, p.cinp);
     }
+    // row limit of every pixel's taps (x and the addend x2 alike)
+    int hn[WPX];
+#pragma unroll
+    for (int j = 0; j < WPX; ++j) hn[j] = RAG ? valid_rows(p.vlen, p.vsh, pn[j], p.H) : p.H;
     for (int tap = 0; tap < taps; ++tap) {
       const int ky = tap / p.kw, kx = tap - (tap / p.kw) * p.kw;
       const T* xb[WPX];
@@ -208,7 +215,7 @@ __global__ __launch_bounds__(256) void conv_igemm(ConvParams p) {
       for (int j = 0; j < WPX; ++j) {
         int hi = pho[j] * p.sh - p.ph + ky * p.dh;
         int wi = pwo[j] * p.sw - p.pw + kx * p.dw;
-        bool ok = pv[j] && hi >= 0 && hi < p.H && wi >= 0 && wi < p.W;
+        bool ok = pv[j] && hi >= 0 && hi < hn[j] && wi >= 0 && wi < p.W;
         size_t pix = ((size_t)pn[j] * p.H + hi) * p.W + wi;
         xb[j] = ok ? X + pix * p.ldx : nullptr;
         xb2[j] = (ok && X2) ? X2 + pix * p.ldx2 : nullptr;
@@ -900,6 +907,12 @@ __global__ __launch_bounds__(64 * NW) void split_chain(ChainParams q) {
   const int r0 = (blockIdx.x - n * tiles_img) * R;
   const int rbase = r0 - nst;                       // image row of buffer row 0
   const int nrows = R + 2 * nst;
+  // ragged batch: the utterance ends at row Hn; the rows from there on are
+  // handled exactly like the rows outside the image (read as zeros, every
+  // stage's output there enters the next stage as zeros, never stored), so a
+  // tile wholly past the end has nothing to do
+  const int Hn = valid_rows(q.vlen, q.vsh, n, H);
+  if (r0 >= Hn) return;
   char* buf0 = smem;
   char* buf1 = smem + q.buf_bytes;
   char* wts = smem + 2 * q.buf_bytes;
@@ -948,7 +961,7 @@ __global__ __launch_bounds__(64 * NW) void split_chain(ChainParams q) {
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
           const int rr = row + r;
-          v[r] = (rr < rb && rr >= 0 && rr < H)
+          v[r] = (rr < rb && rr >= 0 && rr < Hn)
                      ? *reinterpret_cast<const uint4*>(src + (size_t)rr * W * q.lda)
                      : make_uint4(0, 0, 0, 0);
         }
@@ -1006,7 +1019,7 @@ __global__ __launch_bounds__(64 * NW) void split_chain(ChainParams q) {
           const int rr = oa + c / rowchunks;
           const int cc = c - (c / rowchunks) * rowchunks;
           const int px = cc / cu, uu = cc - (cc / cu) * cu;
-          if (rr >= 0 && rr < H)
+          if (rr >= 0 && rr < Hn)
             xr[r] = *reinterpret_cast<const uint4*>(A + (img + (size_t)rr * W + px) * q.lda +
                                                     (k + 1) * w + uu * 8);
         }
@@ -1028,7 +1041,7 @@ __global__ __launch_bounds__(64 * NW) void split_chain(ChainParams q) {
         const int l = pv[j] ? lp : npix - 1;       // clamp: reads stay in the buffer
         prow[j] = oa + l / W;
         pcol[j] = l - (l / W) * W;
-        pv[j] = pv[j] && prow[j] >= 0 && prow[j] < H;
+        pv[j] = pv[j] && prow[j] >= 0 && prow[j] < Hn;
         base[j] = (prow[j] - rbase) * rowb + (pcol[j] + 1) * q.astr;
       }
       f32x4 acc[WCO][WPX];
@@ -1071,7 +1084,7 @@ __global__ __launch_bounds__(64 * NW) void split_chain(ChainParams q) {
     __syncthreads();
     if (more) {
       // combine pass: z_{k+1} = x_{k+1} + y_k (bf16, as the unfused path);
-      // rows outside the image stay zero
+      // rows outside the image (or past the utterance's end) stay zero
 #pragma unroll
       for (int r = 0; r < XREG; ++r) {
         const int c = tid + r * NT;
@@ -1080,7 +1093,7 @@ __global__ __launch_bounds__(64 * NW) void split_chain(ChainParams q) {
           const int cc = c - (c / rowchunks) * rowchunks;
           const int px = cc / cu, uu = cc - (cc / cu) * cu;
           uint4* zp = reinterpret_cast<uint4*>(out + (rr - rbase) * rowb + (px + 1) * q.astr + uu * 16);
-          if (rr >= 0 && rr < H) {
+          if (rr >= 0 && rr < Hn) {
             const bf16x8 x = __builtin_bit_cast(bf16x8, xr[r]);
             const bf16x8 y = __builtin_bit_cast(bf16x8, *zp);
             *zp = __builtin_bit_cast(uint4, frag_add(x, y));
@@ -1132,7 +1145,8 @@ __global__ __launch_bounds__(256) void stem_conv1(const float* __restrict__ x, i
                                                   int W, const float* __restrict__ wts, int Cout,
                                                   const float* __restrict__ mean,
                                                   const float* __restrict__ inv,
-                                                  T* __restrict__ y) {
+                                                  T* __restrict__ y,
+                                                  const int* __restrict__ vlen) {
   __shared__ float sw[9 * 64];
   __shared__ float sm[64], si[64];
   for (int i = threadIdx.x; i < 9 * Cout; i += blockDim.x) sw[i] = wts[i];
@@ -1147,11 +1161,13 @@ __global__ __launch_bounds__(256) void stem_conv1(const float* __restrict__ x, i
                                                 : (unsigned)(pix % ((int64_t)H * W));
   const int hi = (int)(hw / (unsigned)W);
   const int wi = (int)(hw - (unsigned)hi * (unsigned)W);
+  // ragged batch: rows past the utterance's frames are its SAME padding
+  const int Hn = vlen ? valid_rows(vlen, 0, (int)((pix - (int64_t)hw) / ((int64_t)H * W)), H) : H;
   float v[9];
 #pragma unroll
   for (int t = 0; t < 9; ++t) {
     const int yy = hi + t / 3 - 1, xx = wi + t % 3 - 1;
-    float a = (yy >= 0 && yy < H && xx >= 0 && xx < W) ? x[pix + (t / 3 - 1) * W + (t % 3 - 1)] : 0.f;
+    float a = (yy >= 0 && yy < Hn && xx >= 0 && xx < W) ? x[pix + (t / 3 - 1) * W + (t % 3 - 1)] : 0.f;
     if constexpr (sizeof(T) == 2) a = (float)(bf16_t)a;
     v[t] = a;
   }
@@ -1355,7 +1371,9 @@ hipError_t launch_stem(DType t, const float* x, int N, int H, int W, const float
                        (bf16_t*)y, vlen);
     return hipGetLastError();
   }
-  if (vlen) return hipErrorInvalidValue;   // ragged batches: the c32 stem only
+  // ragged batches: the bf16 Res2Net stems only (c32 above, any other Cout on
+  // stem_conv1<bf16_t>); the DPN68 stem and the fp32 stem do not mask
+  if (vlen && (t != BF16 || Cout == 10)) return hipErrorInvalidValue;
   if (t == BF16 && Cout == 10) {
     hipLaunchKernelGGL(stem_conv1_small<10>, dim3(g), dim3(256), 0, s, x, N, H, W, wts, mean, inv,
                        (bf16_t*)y);
@@ -1363,10 +1381,10 @@ hipError_t launch_stem(DType t, const float* x, int N, int H, int W, const float
   }
   if (t == BF16)
     hipLaunchKernelGGL(stem_conv1<bf16_t>, dim3(g), dim3(256), 0, s, x, N, H, W, wts, Cout, mean,
-                       inv, (bf16_t*)y);
+                       inv, (bf16_t*)y, vlen);
   else
     hipLaunchKernelGGL(stem_conv1<float>, dim3(g), dim3(256), 0, s, x, N, H, W, wts, Cout, mean,
-                       inv, (float*)y);
+                       inv, (float*)y, (const int*)nullptr);
   return hipGetLastError();
 }
 
@@ -1377,6 +1395,13 @@ template <typename T, int WCO, int WPX>
 static hipError_t launch_t(const ConvParams& p, const ConvLaunch& l, hipStream_t s) {
   const int M = p.N * p.Ho * p.Wo;
   dim3 grid((M + 64 * WPX - 1) / (64 * WPX), p.groups * p.cblocks, l.splitk > 0 ? l.splitk : 1);
+  if constexpr (sizeof(T) == 2) {
+    // ragged batch: the 3x3s mask their taps (1x1s are per pixel)
+    if (l.vec && p.vlen && p.kh > 1) {
+      hipLaunchKernelGGL((conv_igemm<T, WCO, WPX, true, true>), grid, dim3(256), 0, s, p);
+      return hipGetLastError();
+    }
+  }
   if (l.vec)
     hipLaunchKernelGGL((conv_igemm<T, WCO, WPX, true>), grid, dim3(256), 0, s, p);
   else

@@ -110,8 +110,8 @@ class Extractor:
         """Ragged batch (host numpy): x [N,T,F] with utterance i's lens[i]
         frames first and padding after (its values are ignored) -> [N,D], each
         row equal to run() on that utterance alone at T = lens[i]
-        (vox_embed_lens; res2net -- attentive pooling included -- and tdnn
-        bf16 plans)."""
+        (vox_embed_lens; bf16 plans of every res2net geometry -- attentive
+        pooling included -- and of the tdnn; dpn68 and fp32 plans refuse)."""
         x = np.ascontiguousarray(x, dtype=np.float32)
         if x.ndim != 3:
             raise ValueError("expected [N, T, F] features")
@@ -125,8 +125,8 @@ class Extractor:
 
     def supports_lengths(self):
         """Whether this handle's plans take ragged batches (run_lens): probed
-        once with a two-utterance batch (res2net and tdnn bf16 plans do, the
-        attentive-pooling Res2Nets included)."""
+        once with a two-utterance batch (res2net and tdnn bf16 plans do: the
+        c32, c64 and w8_s6 geometries and the attentive-pooling Res2Nets)."""
         if "_rag_ok" not in self.__dict__:
             try:
                 x = np.zeros((2, 64, self.feat_dim), np.float32)
